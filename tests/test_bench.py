@@ -1,6 +1,7 @@
 """bench.py on the GPU: one short run, and the JSON line's contract (the
 driver parses it): metric/value/unit, steps/warmup, roofline of the dominant
-kernel, cpu_baseline with its core count, and every C4 verdict decided."""
+kernel, with --full cpu_baseline with its core count, and every C4 verdict
+decided; a plain run's line and its --dump-outputs files."""
 import json
 import os
 import subprocess
@@ -15,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_line_contract():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--histories", "2000",
-           "--no-c5", "--no-e2e", "--no-small", "--cpu-seconds", "2"]
+           "--full", "--no-c5", "--no-e2e", "--no-small", "--cpu-seconds", "2"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
@@ -35,6 +36,44 @@ def test_bench_line_contract():
     assert d["verdicts"]["Unknown"] == 0 and d["verdicts"]["Ok"] + d["verdicts"]["Illegal"] == 2000
 
 
+def test_plain_run_is_lean_and_dumps_its_outputs(checker, tmp_path):
+    """Without --full the line holds the headline only (no cpu_baseline, C5,
+    C1-C3 or end-to-end leg), and --dump-outputs writes the last timed step's
+    results as float64 .npy files: the arrays a batch over the same histories
+    returns in this process (verdicts, reasons, configurations, rounds and the
+    certified witnesses)."""
+    import numpy as np
+    import s2_verification_amd as s2
+    from s2_verification_amd import workloads as W
+    n = 300
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--histories", str(n), "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "verdicts"):
+        assert k in d, k
+    for k in ("cpu_baseline", "speedup_vs_cpu", "c5", "c1_c3", "end_to_end", "strong_split"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
+    b = checker.batch(W.c4_histories(n))
+    b.run()
+    ref = b.results_flat(with_witness=True)
+    ref["witness_histories"] = np.arange(n)
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert sorted(got) == sorted(ref)
+    for k, a in got.items():
+        assert a.dtype == np.float64 and np.array_equal(a, ref[k].astype(np.float64)), k
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    assert d["verdicts"] == {"Ok": int(np.sum(got["verdict"] == s2.S2LC_OK)),
+                             "Illegal": int(np.sum(got["verdict"] == s2.S2LC_ILLEGAL)), "Unknown": 0}
+    assert got["witness_offs"][-1] == len(got["witness_ids"]) > 0
+
+
 @pytest.mark.gpu
 def test_bench_two_gloo_ranks_on_one_gpu():
     """The driver's multi-GPU bench path, rehearsed with 2 ranks sharing the one
@@ -48,7 +87,7 @@ def test_bench_two_gloo_ranks_on_one_gpu():
     port = random.randint(20000, 40000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-e2e", "--c5-reps", "1"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-e2e", "--c5-reps", "1"]
     env = dict(os.environ, S2LC_BENCH_GLOO="1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-4000:]
@@ -97,7 +136,7 @@ def test_bench_watchdog_keeps_the_c4_line():
     port = random.randint(20000, 40000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-e2e", "--c5-reps", "1"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-e2e", "--c5-reps", "1"]
     env = dict(os.environ, S2LC_BENCH_GLOO="1", S2LC_BENCH_WATCHDOG="0.05")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode != 0, p.stdout[-2000:]

@@ -4,6 +4,7 @@ call sequence of the Go cgo shim in INTEGRATION.md §2. Compiled with gcc
 the in-tree libs2lincheck.so."""
 import os
 import subprocess
+import sys
 
 import pytest
 
@@ -21,9 +22,19 @@ def build(tmp_path):
     return exe
 
 
+def gpu_present():
+    """torch.cuda.is_available() asked in a fresh interpreter. In this process
+    it answers False once an earlier test has opened the device through
+    libs2lincheck (the whole suite in one run on a GPU machine: torch brings a
+    HIP runtime of its own), and the no-GPU sequence then ran beside a GPU."""
+    p = subprocess.run([sys.executable, "-c", "import sys, torch; sys.exit(0 if torch.cuda.is_available() else 3)"],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode in (0, 3), p.stderr[-2000:]
+    return p.returncode == 0
+
+
 def test_c99_caller_without_gpu(tmp_path):
-    import torch
-    if torch.cuda.is_available():
+    if gpu_present():
         pytest.skip("a GPU is present: test_c99_caller_on_gpu covers the full sequence")
     exe = build(tmp_path)
     p = subprocess.run([exe, "--no-gpu"], capture_output=True, text=True, timeout=120)

@@ -13,7 +13,7 @@ for rep in 1 2; do
     i=$((i + 1))
     envs=()
     [ "$v" != "-" ] && read -r -a envs <<< "$v"
-    env "${envs[@]}" timeout -k 10 300 python3 bench.py --no-c5 --no-small --no-cpu-baseline --steps 5 --warmup 2 \
+    env "${envs[@]}" timeout -k 10 300 python3 bench.py --full --no-c5 --no-small --no-cpu-baseline --steps 5 --warmup 2 \
       > "$OUT/e$i.$rep.json" 2> "$OUT/e$i.$rep.err" || { echo "[$v] failed"; tail -3 "$OUT/e$i.$rep.err"; exit 1; }
     echo "$rep [$v] $(python3 -c "
 import json; d=json.load(open('$OUT/e$i.$rep.json')); e=d['end_to_end']; w=e['warm']

@@ -10,6 +10,6 @@ timeout -k 10 600 python3 -u -m pytest -x -v --timeout 300 --timeout-method thre
   tests/test_engines.py tests/test_c4_full.py > "$OUT/pytest.txt" 2>&1 || { tail -5 "$OUT/pytest.txt"; exit 1; }
 tail -1 "$OUT/pytest.txt"
 for r in 1 2; do
-  timeout -k 10 300 python3 bench.py --no-c5 --no-small --no-cpu-baseline > "$OUT/b$r.json" 2> "$OUT/b$r.err" || exit 1
-  S2LC_PACK_SMALL=0 timeout -k 10 300 python3 bench.py --no-c5 --no-small --no-cpu-baseline > "$OUT/o$r.json" 2> "$OUT/o$r.err" || exit 1
+  timeout -k 10 300 python3 bench.py --full --no-c5 --no-small --no-cpu-baseline > "$OUT/b$r.json" 2> "$OUT/b$r.err" || exit 1
+  S2LC_PACK_SMALL=0 timeout -k 10 300 python3 bench.py --full --no-c5 --no-small --no-cpu-baseline > "$OUT/o$r.json" 2> "$OUT/o$r.err" || exit 1
 done
