@@ -228,6 +228,27 @@ int s2lc_load_jsonl(const char* path_or_dash, const uint8_t* buf, size_t len,
  * out[i] is NULL, *err_index names the buffer and err its decode error. */
 int s2lc_load_jsonl_many(const uint8_t* const* bufs, const size_t* lens, size_t n, int n_threads,
                          s2lc_history** out, size_t* err_index, char* err, size_t errlen);
+/* s2lc_load_jsonl_many with the per-byte scan on ctx's device (opt-in). The
+ * buffers are staged in chunks (S2LC_DEVDECODE_CHUNK_MB, default 512) through
+ * pinned memory; the device decodes every history entirely in the collector's
+ * serialisation (records separated by exactly one '\n', at most 512 chains, 64
+ * distinct fencing tokens of at most 64 bytes) into a binary cache section,
+ * which is loaded with every check s2lc_history_load_many makes. Any other
+ * history is decoded on the host exactly as s2lc_load_jsonl_many decodes it,
+ * so the histories and the errors are the same either way. on_device[i] (when
+ * not NULL) is 1 for a history the device decoded. Same all-or-nothing
+ * contract; the message ("history <i>: ...") is read with s2lc_last_error. */
+typedef struct s2lc_decode_stats {
+  uint32_t struct_size;    /* sizeof(s2lc_decode_stats), set by the caller */
+  uint32_t n_device;       /* histories decoded on the device */
+  uint32_t n_fallback;     /* histories decoded on the host */
+  uint32_t n_rejected;     /* of those: a device section the load checks refused (a decoder bug) */
+  uint64_t bytes_in, bytes_out; /* text uploaded, section bytes downloaded */
+  double stage_ms, h2d_ms, kernel_ms, d2h_ms, load_ms; /* kernel_ms, h2d_ms, d2h_ms: HIP events */
+} s2lc_decode_stats;
+int s2lc_load_jsonl_many_device(s2lc_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n,
+                                int n_threads, s2lc_history** out, uint8_t* on_device /* [n] or NULL */,
+                                s2lc_decode_stats* stats /* or NULL */, size_t* err_index);
 /* Build a history from porcupine-style events; all buffers are copied. */
 int s2lc_history_from_events(const s2lc_event* events, size_t n_events,
                              s2lc_history** out, char* err, size_t errlen);

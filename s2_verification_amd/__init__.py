@@ -114,6 +114,13 @@ class c_batch_stats(ctypes.Structure):
                 ("level_solo_ms", ctypes.c_double), ("level_grows", ctypes.c_uint32), ("_pad5", ctypes.c_uint32)]
 
 
+class c_decode_stats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_device", ctypes.c_uint32), ("n_fallback", ctypes.c_uint32),
+                ("n_rejected", ctypes.c_uint32), ("bytes_in", ctypes.c_uint64), ("bytes_out", ctypes.c_uint64),
+                ("stage_ms", ctypes.c_double), ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("d2h_ms", ctypes.c_double), ("load_ms", ctypes.c_double)]
+
+
 class c_sim_params(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("workflow", ctypes.c_uint32),
                 ("num_clients", ctypes.c_uint32), ("ops_per_client", ctypes.c_uint32),
@@ -208,6 +215,9 @@ SIGNATURES = [
     ("s2lc_load_jsonl_many", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                             ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_P),
                                             ctypes.POINTER(ctypes.c_size_t), ctypes.c_char_p, ctypes.c_size_t]),
+    ("s2lc_load_jsonl_many_device", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p),
+                                                   ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_int,
+                                                   ctypes.POINTER(_P), _P, _P, ctypes.POINTER(ctypes.c_size_t)]),
     ("s2lc_visualize", ctypes.c_int, [_P, ctypes.POINTER(c_result), ctypes.c_char_p]),
     ("s2lc_describe_operation", ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
     ("s2lc_describe_state", ctypes.c_int, [_P, ctypes.POINTER(c_state), ctypes.c_char_p, ctypes.c_size_t]),
@@ -762,8 +772,34 @@ class Checker:
     def check_batch(self, hs: Sequence[History]) -> List[CheckResult]:
         return Batch(self, hs).check()
 
+    def load_jsonl_many(self, blobs: Sequence[bytes], threads: int = 0) -> Tuple[List[History], dict]:
+        """s2lc_load_jsonl_many_device: load_many with the per-byte scan on
+        this checker's device. Histories entirely in the collector's form are
+        decoded there into cache sections; any other is decoded on the host, so
+        the histories (and the error raised) are load_many's. Returns them
+        with the call's stats: the s2lc_decode_stats fields and "on_device",
+        a uint8 array with 1 for each history the device decoded."""
+        n = len(blobs)
+        keep = [b if type(b) is bytes else bytes(b) for b in blobs]
+        arr = (ctypes.c_char_p * max(1, n))(*keep)
+        bufs = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
+        lens = np.fromiter(map(len, keep), np.uint64, n) if n else np.zeros(1, np.uint64)
+        out = np.zeros(max(1, n), np.uint64)
+        on_dev = np.zeros(max(1, n), np.uint8)
+        st = c_decode_stats()
+        st.struct_size = ctypes.sizeof(c_decode_stats)
+        bad = ctypes.c_size_t(0)
+        rc = lib().s2lc_load_jsonl_many_device(self._ctx, bufs, lens.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+                                               n, threads, out.ctypes.data_as(ctypes.POINTER(_P)),
+                                               on_dev.ctypes.data, ctypes.addressof(st), ctypes.byref(bad))
+        if rc:
+            raise S2LCError(rc, self.last_error())
+        stats = {name: getattr(st, name) for name, _ in c_decode_stats._fields_ if name != "struct_size"}
+        stats["on_device"] = on_dev[:n]
+        return list(map(History, out[:n].tolist())), stats
+
     def check_jsonl_many(self, blobs: Sequence[bytes], threads: int = 0, slices: int = 2,
-                         with_witness: bool = True, overlap: Optional[bool] = None) -> dict:
+                         with_witness: bool = True, overlap: Optional[bool] = None, decode: str = "host") -> dict:
         """Collector JSONL blobs (one history each) -> Batch.results_flat's
         arrays, in input order, pipelined over `slices` slices of the input:
         slice k+1 decodes on the host cores while slice k uploads and runs on
@@ -780,9 +816,13 @@ class Checker:
         run on different threads, so each takes the checker's lock around its
         context calls (they had shared the context's error slot and
         its stream unguarded). The decode (s2lc_load_jsonl_many) needs no
-        context and runs beside either."""
+        context and runs beside either. decode="device" decodes each slice with
+        load_jsonl_many instead (opt-in; the same histories): that is a context
+        call, so it takes the lock too."""
         import threading
         from concurrent.futures import ThreadPoolExecutor
+        if decode not in ("host", "device"):
+            raise ValueError('decode must be "host" or "device"')
         n = len(blobs)
         S = max(1, min(int(slices), n))
         cuts = [n * k // S for k in range(S + 1)]
@@ -819,7 +859,11 @@ class Checker:
             fut = None
             slot_cert = [None, None]  # (overlap) the pending certification of each device batch
             for k in range(S):
-                hs = load_many(blobs[cuts[k]:cuts[k + 1]], threads=threads)  # (ctypes: the GIL is released)
+                if decode == "device":
+                    with lock:
+                        hs = self.load_jsonl_many(blobs[cuts[k]:cuts[k + 1]], threads=threads)[0]
+                else:
+                    hs = load_many(blobs[cuts[k]:cuts[k + 1]], threads=threads)  # (ctypes: the GIL is released)
                 prev = fut.result() if fut is not None else None
                 if overlap:
                     if prev is not None:

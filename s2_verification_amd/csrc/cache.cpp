@@ -83,10 +83,7 @@ bool event_eq(const Event& a, const Event& b) {  // field by field (padding byte
          a.has_hash == b.has_hash && a.tail == b.tail && a.stream_hash == b.stream_hash;
 }
 
-struct Head {
-  uint32_t status, structural, n_ops, n_ident, K, hflags, max_chain_len, n_tokens;
-  uint64_t n_events, n_pool, n_recs, mode, n_cs;  // n_cs: chain_start entries (K + 1, or 0 unfinalized)
-};
+using Head = CacheHead;
 
 // A history whose events are exactly its ops' call / return pairs, each
 // event's fields those of its op's record (true for every finalized history
@@ -308,6 +305,8 @@ bool read_section(const uint8_t* p, const uint8_t* end, History& h) {
 }
 
 }  // namespace
+
+bool cache_section_load(const uint8_t* p, const uint8_t* end, History& h) { return read_section(p, end, h); }
 
 void History::ensure_events() const {
   if (!lazy_once) return;

@@ -21,9 +21,13 @@
 #include "search.h"
 #include "cert_prof.h"
 #include "host_par.h"
+#include "jsonl_dev.h"
 
 namespace s2lc {
 int simulate(const s2lc_sim_params& p, History* h, std::string* jsonl);
+int jd_decode_many(JdState** state, int device, const uint8_t* const* bufs, const size_t* lens, size_t n,
+                   int n_threads, s2lc_history** pre, uint8_t* on_device, JdStats& st, std::vector<int>& rcs,
+                   std::vector<std::string>& errs, std::string& err);
 }
 
 using namespace s2lc;
@@ -53,6 +57,7 @@ struct s2lc_ctx {
   std::vector<int> devices;                    // s2lc_check_batch shards (>= 1 entries)
   std::vector<std::unique_ptr<Shard>> shards;  // created lazily, one per devices entry
   std::string err;
+  JdState* jd = nullptr;  // s2lc_load_jsonl_many_device's stage and device buffers (grow-only)
 
   RunOpts run_opts() const {
     RunOpts r;
@@ -157,6 +162,7 @@ void s2lc_destroy(s2lc_ctx* c) {
     if (sh->own_stream && sh->stream) (void)hipStreamDestroy(sh->stream);
   }
   (void)hipSetDevice(c->device);
+  jd_release(c->jd);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -258,6 +264,70 @@ int s2lc_load_jsonl_many(const uint8_t* const* bufs, const size_t* lens, size_t 
     return rcs[bad];
   }
   return 0;
+}
+
+int s2lc_load_jsonl_many_device(s2lc_ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, int n_threads,
+                                s2lc_history** out, uint8_t* on_device, s2lc_decode_stats* stats, size_t* err_index) {
+  if (!c) return S2LC_EINVAL;
+  if (!out || (n && (!bufs || !lens))) {
+    c->err = "bad argument";
+    return S2LC_EINVAL;
+  }
+  for (size_t i = 0; i < n; ++i) out[i] = nullptr;
+  if (on_device && n) memset(on_device, 0, n);
+  if (stats) {
+    const uint32_t sz = stats->struct_size;
+    if (sz < sizeof(s2lc_decode_stats)) {
+      c->err = "s2lc_decode_stats.struct_size too small";
+      return S2LC_EINVAL;
+    }
+    memset(stats, 0, sizeof *stats);
+    stats->struct_size = sz;
+  }
+  if (!n) return 0;
+  try {
+    std::vector<s2lc_history*> pre(n, nullptr);
+    history_acquire_many(n, pre.data());
+    std::vector<int> rcs(n, 0);
+    std::vector<std::string> errs(n);
+    JdStats st;
+    int rc = jd_decode_many(&c->jd, c->device, bufs, lens, n, n_threads, pre.data(), on_device, st, rcs, errs, c->err);
+    size_t bad = SIZE_MAX;
+    if (!rc) {
+      for (size_t i = 0; i < n && bad == SIZE_MAX; ++i)
+        if (rcs[i]) bad = i;
+      if (bad != SIZE_MAX) {
+        rc = rcs[bad];
+        if (err_index) *err_index = bad;
+        c->err = "history " + std::to_string(bad) + ": " + errs[bad];
+      }
+    }
+    if (rc) {
+      for (size_t i = 0; i < n; ++i) history_release(pre[i]);
+      if (on_device) memset(on_device, 0, n);
+      return rc;
+    }
+    for (size_t i = 0; i < n; ++i) out[i] = pre[i];
+    if (stats) {
+      stats->n_device = st.n_device;
+      stats->n_fallback = st.n_fallback;
+      stats->n_rejected = st.n_rejected;
+      stats->bytes_in = st.bytes_in;
+      stats->bytes_out = st.bytes_out;
+      stats->stage_ms = st.stage_ms;
+      stats->h2d_ms = st.h2d_ms;
+      stats->kernel_ms = st.kernel_ms;
+      stats->d2h_ms = st.d2h_ms;
+      stats->load_ms = st.load_ms;
+    }
+    return 0;
+  } catch (const std::bad_alloc&) {
+    c->err = "out of memory";
+    return S2LC_ENOMEM;
+  } catch (...) {
+    c->err = "internal error";
+    return S2LC_EINVAL;
+  }
 }
 
 int s2lc_history_from_events(const s2lc_event* ev, size_t n, s2lc_history** out, char* err, size_t errlen) {

@@ -129,6 +129,12 @@ int load_jsonl(const uint8_t* buf, size_t len, History& h, std::string& err);
 // own every error message. Returns 0 or the status; the message in err.
 int load_jsonl_finalized(const uint8_t* buf, size_t len, History& h, std::string& err);
 
+// One history from its cache section [p, end), with every check
+// s2lc_history_load_many makes; false on a malformed section (h is then in an
+// unspecified state: recycle() it). The device JSONL decoder loads its
+// sections through this.
+bool cache_section_load(const uint8_t* p, const uint8_t* end, History& h);
+
 // Deterministic simulator (collector workload, history.rs + collect-history.rs).
 struct SimParams;
 }  // namespace s2lc

@@ -47,6 +47,13 @@ struct __attribute__((aligned(64))) OpRec {
 };
 static_assert(sizeof(OpRec) == 64, "OpRec must be 64 bytes");
 
+// The head of one history's section in the binary cache image (cache.cpp).
+struct CacheHead {
+  uint32_t status, structural, n_ops, n_ident, K, hflags, max_chain_len, n_tokens;
+  uint64_t n_events, n_pool, n_recs, mode, n_cs;  // n_cs: chain_start entries (K + 1, or 0 unfinalized)
+};
+static_assert(sizeof(CacheHead) == 72, "cache section head");
+
 struct State {
   uint64_t tail;
   uint64_t hash;
